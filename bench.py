@@ -2,6 +2,12 @@
 """bench.py — stage-1 CSV structural indexing throughput on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--gib-per-gpu G] [--skew B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given
+(see dump_outputs) and prints the headline line: `value` (whole-job GiB/s) and `ms_per_step`.  Everything else this
+docstring describes below — the verification of the timed tape, the roofline leg, the q10 and strong-scaling legs, the
+other workloads, batch / consumers / latency / ingest legs and the CPU baselines — runs only with --full.
 
 A "step" is one pass of the hot path over one batch of synthetic CSV already resident in HBM:
 each rank indexes its contiguous byte shard of the file (first stage-1 launch through the C ABI: rank 0
@@ -14,7 +20,7 @@ launch and the final copy-out waits for the host; the step ends when the tape an
 final on every rank.  Weak scaling: every rank always holds the same number of bytes (default 8 GiB =
 one GPU's shard of BASELINE config 4, "64 GiB synthetic CSV, 64 cols, chunk-sharded 8xMI355X").
 
-The timed path is VERIFIED at every N (the line carries "verified", the process exits non-zero on a
+With --full the timed path is VERIFIED at every N (the line carries "verified", the process exits non-zero on a
 mismatch): each rank compares its whole tape shard, entry for entry, with an independent restatement of
 the definition in plain torch ops on the same device bytes (and with the closed form on quote-free
 corpora), compares 1 Mi entries either side of its shard boundaries and an order-sensitive checksum
@@ -1343,6 +1349,97 @@ def verify_everything(oracle, sb, state, dist_on, rank, world):
     return out
 
 
+def roofline_leg(sb, state, workload, steps, dist_on, world, rank):
+    """--full: the stage-1 kernel alone, HIP events on its own stream, on EVERY rank, next to rank 0's bare-stream
+    probe of the same buffer.  Runs launches of its own after the timed steps."""
+    import torch.distributed as dist
+    kern_ms_mine = kernel_time_ms(sb, max(5, min(steps, 50)))
+    per_rank_ms = [kern_ms_mine]
+    if dist_on:
+        gathered_ms = [None] * world
+        dist.all_gather_object(gathered_ms, float(kern_ms_mine))
+        per_rank_ms = [float(x) for x in gathered_ms]
+    # the slowest rank's kernel prices the job (at N = 1 that is the only one)
+    kern_ms = max(per_rank_ms)
+    achieved = sb.n / (kern_ms * 1e-3) / 1e9
+    entries = state["count"]
+    # what this GPU's HBM actually streams with the same traffic shape and no work at all (the tape
+    # shard doubles as the probe's output buffer: it is rewritten by the next launch anyway); rank 0's GPU only
+    probed = None
+    if rank == 0 and sb.cap * 8 >= sb.n // 4:
+        s_ = sb.stream()
+        ms_r = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 0, s_, 1, 5)
+        ms_rw = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 4, s_, 1, 5)
+        ms_rw2 = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 4, s_, 1, 5, blocks_per_cu=2)
+        probed = {"read_only_GBps": round(sb.n / (ms_r * 1e-3) / 1e9, 1),
+                  "read_with_quarter_written_GBps": round(sb.n / (ms_rw * 1e-3) / 1e9, 1),
+                  "read_with_quarter_written_8_waves_per_cu_GBps": round(sb.n / (ms_rw2 * 1e-3) / 1e9, 1),
+                  "kernel_vs_probe": round(sb.n / (kern_ms_mine * 1e-3) / 1e9 / (sb.n / (ms_rw * 1e-3) / 1e9), 3),
+                  "gpu": "rank 0's",
+                  "note": "bare nt stream of the same buffer with none of the work (csvsimd_hbm_probe_device), at the "
+                          "kernel's 16 waves/CU and at the 8 waves/CU where a bare stream peaks; the 64x31 corpus "
+                          "writes 8 B of tape per 32 B read"}
+    roofline = {
+        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": load_traffic(workload, sb.n),
+        "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)",
+        "kernel": sb.ctx.kernel_name(), "kernels_per_launch": 1, "kernel_ms": round(kern_ms, 4),
+        "kernel_ms_per_rank": {"min": round(min(per_rank_ms), 4), "max": round(max(per_rank_ms), 4),
+                               "all": [round(x, 4) for x in per_rank_ms],
+                               "note": "every rank times its own launches (HIP events on its stream); `kernel_ms`, "
+                                       "`achieved` and `frac` are the SLOWEST rank's"},
+        "entry_point": "csvsimd_stage1_time_device -> launch_stage1 (the product library; probe builds refused)",
+        "algorithmic_bytes_per_launch": sb.n,
+        "read_plus_tape_write_GBps": round((sb.n + 8 * entries) / (kern_ms * 1e-3) / 1e9, 1),
+        "probed_stream": probed,
+    }
+    return roofline
+
+
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step handed its caller, so that two builds can be compared
+# ------------------------------------------------------------------------------------------------
+DUMP_ENTRIES = 1 << 20   # entries per tape file, all ranks together: five files of 8 MB at most
+DUMP_SEED = 1729
+
+
+def dump_outputs(outdir, sb, state, rank, world):
+    """Writes this rank's result of the LAST timed step as float64 .npy files (offsets and sums below 2**53: exact).
+        record.npy              [count, in_quote_in, tape_index_base, total_entries, in_quote_final]
+        tape_head.npy           the first entries of the tape shard
+        tape_tail.npy           its last entries
+        tape_sample_index.npy   one position in each of equally many equal strata of the tape, at a seeded offset
+        tape_sample.npy         the entries at those positions
+        tape_block_sums.npy     sums of consecutive blocks of entries: every entry of the tape counts
+    With N > 1 every rank writes its own files, named rank<r>_<name>.npy.  The corpus and the sample positions follow
+    from the arguments alone, so the files of two runs with the same arguments compare entry for entry."""
+    count = int(state["count"])
+    tape = sb.dtape[:count]
+    per = max(1, DUMP_ENTRIES // world)
+    out = {"record": np.array([count, state["inq"], state["base"], state["total"], state["final"]], dtype=np.float64),
+           "tape_head": tape[:per], "tape_tail": tape[max(0, count - per):]}
+    if count <= per:
+        idx = np.arange(count, dtype=np.int64)
+    else:
+        stride = count // per
+        idx = np.arange(per, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED + rank).integers(0, stride, per)
+    out["tape_sample_index"] = idx.astype(np.float64)
+    out["tape_sample"] = tape[torch.from_numpy(idx).to(tape.device)]
+    block = max(1, -(-count // per))
+    whole = count // block * block
+    sums = tape[:whole].view(-1, block).sum(1)
+    if whole < count:
+        sums = torch.cat([sums, tape[whole:].sum().view(1)])
+    assert count == 0 or int(tape[-1]) * block < 2**53, "block sums would not be exact in float64"
+    out["tape_block_sums"] = sums
+    os.makedirs(outdir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in out.items():
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        np.save(os.path.join(outdir, f"{prefix}{name}.npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1377,6 +1474,13 @@ def main():
     ap.add_argument("--only-consumers", action="store_true",
                     help="development / profiling: run the `consumers` leg alone and print its record (not the "
                          "contract line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, "
+                         "< 64 MB; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: verification, roofline, the q10 and strong-scaling legs, "
+                         "other workloads, batch, consumers, latency, ingest and the CPU baselines (each still subject "
+                         "to its --no-* option)")
     args = ap.parse_args()
     if os.environ.get("CSVSIMD_BENCH_WATCHDOG"):   # development: where is a stuck run stuck?
         import faulthandler
@@ -1430,7 +1534,8 @@ def main():
     pkg = graft.load_package()
     refuse_probe_environment(pkg)
     from csv_simd_amd import sharded
-    oracle = graft.load_oracle() if not (args.no_verify and args.no_cpu_baseline) else None
+    full = args.full
+    oracle = graft.load_oracle() if (full and not (args.no_verify and args.no_cpu_baseline)) else None
     if args.only_consumers:
         print(json.dumps({"consumers": consumers_leg(pkg, oracle or graft.load_oracle(), device)}))
         return
@@ -1471,50 +1576,12 @@ def main():
     total_bytes = sb.total
     gib_s = total_bytes * args.steps / dt / 2**30
     rows = total_bytes // sb.row
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sb, state, rank, world)
 
-    verified = None if args.no_verify else verify_everything(oracle, sb, state, dist_on, rank, world)
+    verified = None if (args.no_verify or not full) else verify_everything(oracle, sb, state, dist_on, rank, world)
 
-    # ---- roofline leg: the stage-1 kernel alone, HIP events on its own stream, on EVERY rank -------
-    kern_ms_mine = kernel_time_ms(sb, max(5, min(args.steps, 50)))
-    per_rank_ms = [kern_ms_mine]
-    if dist_on:
-        gathered_ms = [None] * world
-        dist.all_gather_object(gathered_ms, float(kern_ms_mine))
-        per_rank_ms = [float(x) for x in gathered_ms]
-    # the slowest rank's kernel prices the job (at N = 1 that is the only one)
-    kern_ms = max(per_rank_ms)
-    achieved = sb.n / (kern_ms * 1e-3) / 1e9
-    entries = state["count"]
-    # what this GPU's HBM actually streams with the same traffic shape and no work at all (the tape
-    # shard doubles as the probe's output buffer: it is rewritten by the next launch anyway); rank 0's GPU only
-    probed = None
-    if rank == 0 and sb.cap * 8 >= sb.n // 4:
-        s_ = sb.stream()
-        ms_r = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 0, s_, 1, 5)
-        ms_rw = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 4, s_, 1, 5)
-        ms_rw2 = sb.ctx.hbm_probe_device(sb.dbuf.data_ptr(), sb.n, sb.dtape.data_ptr(), 4, s_, 1, 5, blocks_per_cu=2)
-        probed = {"read_only_GBps": round(sb.n / (ms_r * 1e-3) / 1e9, 1),
-                  "read_with_quarter_written_GBps": round(sb.n / (ms_rw * 1e-3) / 1e9, 1),
-                  "read_with_quarter_written_8_waves_per_cu_GBps": round(sb.n / (ms_rw2 * 1e-3) / 1e9, 1),
-                  "kernel_vs_probe": round(sb.n / (kern_ms_mine * 1e-3) / 1e9 / (sb.n / (ms_rw * 1e-3) / 1e9), 3),
-                  "gpu": "rank 0's",
-                  "note": "bare nt stream of the same buffer with none of the work (csvsimd_hbm_probe_device), at the "
-                          "kernel's 16 waves/CU and at the 8 waves/CU where a bare stream peaks; the 64x31 corpus "
-                          "writes 8 B of tape per 32 B read"}
-    roofline = {
-        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": load_traffic(args.workload, sb.n),
-        "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)",
-        "kernel": sb.ctx.kernel_name(), "kernels_per_launch": 1, "kernel_ms": round(kern_ms, 4),
-        "kernel_ms_per_rank": {"min": round(min(per_rank_ms), 4), "max": round(max(per_rank_ms), 4),
-                               "all": [round(x, 4) for x in per_rank_ms],
-                               "note": "every rank times its own launches (HIP events on its stream); `kernel_ms`, "
-                                       "`achieved` and `frac` are the SLOWEST rank's"},
-        "entry_point": "csvsimd_stage1_time_device -> launch_stage1 (the product library; probe builds refused)",
-        "algorithmic_bytes_per_launch": sb.n,
-        "read_plus_tape_write_GBps": round((sb.n + 8 * entries) / (kern_ms * 1e-3) / 1e9, 1),
-        "probed_stream": probed,
-    }
+    roofline = roofline_leg(sb, state, args.workload, args.steps, dist_on, world, rank) if full else None
 
     if dist_on:
         backend = dist.get_backend()
@@ -1550,16 +1617,17 @@ def main():
         "gib_per_s_per_gpu": round(gib_s / world, 3),
         "verified": verified,
         "roofline": roofline,
+        "full": full,   # False: the headline alone (no verification, roofline or other legs: --full)
     }
 
     # the first 2 GiB of rank 0's shard, on the host, for the CPU baselines and the ingest leg (taken before the
     # device buffers are recycled by the legs below)
-    sample = host_sample(sb, 2 << 30) if (rank == 0 and not (args.no_cpu_baseline and args.no_ingest)) else None
+    sample = host_sample(sb, 2 << 30) if (full and rank == 0 and not (args.no_cpu_baseline and args.no_ingest)) else None
     main_width, main_q, main_lo = sb.width, sb.q, sb.lo
 
     # ---- the quoted corpus, cut mid-row: the stitch is non-trivial and ranks re-emit -------------
     failed = verified is not None and not (verified["tape"] and verified["stitch"])
-    if not args.no_q10_check and args.workload == "64x31_noquote" and not args.no_verify and not strong:
+    if full and not args.no_q10_check and args.workload == "64x31_noquote" and not args.no_verify and not strong:
         sb.release()
         cuts = mid_row_cuts(oracle, pkg, "64x31_q10", shard_bytes, world)
         sbq = ShardBench(pkg, device, "64x31_q10", shard_bytes, rank, world, cuts=cuts, depth=sb_depth)
@@ -1584,7 +1652,7 @@ def main():
     # (the default line is weak scaling: 8 GiB per GPU at every N.  This leg indexes the SAME 64 GiB file at every N —
     # all of it on one GPU at N = 1, 8 GiB each at N = 8 — so the driver's N = 1, 2, 4, 8 runs also hold the
     # speed-up on one file, verified like the main leg.)
-    if not args.no_strong_check and args.workload == "64x31_noquote" and not strong and not args.no_verify:
+    if full and not args.no_strong_check and args.workload == "64x31_noquote" and not strong and not args.no_verify:
         strong_total = int(args.total_gib * 2**30)
         if strong_total // world == shard_bytes:
             out["strong_scaling_check"] = {"total_GiB": args.total_gib, "identical_to_main_leg": True,
@@ -1608,7 +1676,7 @@ def main():
             sbs.release()
             del sbs
 
-    if rank == 0 and world == 1:
+    if full and rank == 0 and world == 1:
         sb.release()
         if not args.no_extra:
             extra = {}
@@ -1650,7 +1718,7 @@ def main():
             out["small_files"] = small_files_leg(pkg, oracle, device)
             failed = failed or not out["small_files"]["verified"]
     # ---- the CPU beside it, same bytes, same run, at EVERY N (rank 0's host cores) -------------------------------
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(oracle, sample)
         out.update(cpu_baseline_variants(oracle, sample, main_width))
     if rank == 0:

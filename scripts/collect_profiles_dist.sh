@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/prof_dist
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 export CSVSIMD_BENCH_FORCE_DIST=1
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $REPO/bench.py --steps 10 --warmup 2 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 $REPO/bench.py --full --steps 10 --warmup 2 \
     --no-extra --no-cpu-baseline --no-verify --no-q10-check --no-ingest > "$OUT/stats.log" 2>&1
 find "$OUT/stats" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_dist_world1.csv" \;
 find "$OUT" -name "*kernel_trace.csv" -delete

@@ -8,7 +8,7 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/ext" -- python3 $REPO/scripts/probe_dialect.py 4 > "$OUT/ext.log" 2>&1
 find "$OUT/ext" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats_extensions.csv" \;
-BENCH="python3 $REPO/bench.py --workload 1024x4_dense --gib-per-gpu 1 --steps 10 --warmup 2 --no-extra --no-cpu-baseline"
+BENCH="python3 $REPO/bench.py --full --workload 1024x4_dense --gib-per-gpu 1 --steps 10 --warmup 2 --no-extra --no-cpu-baseline"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_WR"; do
     i=$((i + 1))

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_r04_16x32
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-FLAGS="--gib-per-gpu 1 --steps 20 --warmup 3 --no-extra --no-cpu-baseline --no-verify --no-q10-check --no-ingest --no-strong-check"
+FLAGS="--full --gib-per-gpu 1 --steps 20 --warmup 3 --no-extra --no-cpu-baseline --no-verify --no-q10-check --no-ingest --no-strong-check"
 for W in 16x32_noquote 16x32_q10; do
     CMD="python3 $REPO/bench.py --workload $W $FLAGS"
     rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$W" -- $CMD > "$OUT/stats_$W.log" 2>&1

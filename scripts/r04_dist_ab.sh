@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/r04_dist_ab
 mkdir -p "$OUT"
 cd $REPO
-COMMON="--steps 100 --warmup 3 --no-extra --no-cpu-baseline --no-q10-check --no-ingest --no-strong-check --no-verify"
+COMMON="--full --steps 100 --warmup 3 --no-extra --no-cpu-baseline --no-q10-check --no-ingest --no-strong-check --no-verify"
 for rep in 1 2 3; do
   timeout -k 10 300 python3 bench.py $COMMON > "$OUT/plain_$rep.json" 2> "$OUT/plain_$rep.err" || echo "plain failed"
   CSVSIMD_BENCH_FORCE_DIST=1 timeout -k 10 300 python3 bench.py $COMMON > "$OUT/overlap_$rep.json" 2> "$OUT/overlap_$rep.err" || echo "overlap failed"

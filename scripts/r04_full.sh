@@ -8,7 +8,7 @@ cd $REPO
 timeout -k 10 1000 python -m pytest tests/ -x -q -m gpu --durations=8 > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"
 tail -14 "$OUT/pytest.log"
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout -k 10 600 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -3 "$OUT/bench.err"
+timeout -k 10 600 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -3 "$OUT/bench.err"
 python3 - <<'PY'
 import json,os
 out=os.environ.get("GRAFT_REPO_ROOT","/root/repo")+"/gpurun_out/r04_full/"

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 export CSVSIMD_BENCH_FORCE_DIST=1
 for mode in 1; do
   export CSVSIMD_BENCH_TAIL_OVERLAP=$mode
-  rocprofv3 --kernel-trace --output-format csv -d "$OUT/t$mode" -- python3 $REPO/bench.py --steps 12 --warmup 2 \
+  rocprofv3 --kernel-trace --output-format csv -d "$OUT/t$mode" -- python3 $REPO/bench.py --full --steps 12 --warmup 2 \
       --no-extra --no-cpu-baseline --no-verify --no-q10-check --no-ingest --no-strong-check > "$OUT/t$mode.log" 2>&1
   echo "mode $mode rc=$?"
   f=$(find "$OUT/t$mode" -name "*kernel_trace.csv" | head -1)

@@ -19,6 +19,10 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def pkg():
+    # torch before the library: torch brings its own HIP runtime (torch/lib/libamdhip64.so), which the library then
+    # shares through its soname.  Loaded the other way round, the process maps two HIP runtimes, and the one initialised
+    # second (the library's, once torch has touched the GPU) finds no device.
+    import torch  # noqa: F401
     so = os.path.join(ROOT, "csv-simd_amd", "csrc", "libcsvsimd_hip.so")
     if not os.path.exists(so):
         graft.build()

@@ -75,6 +75,16 @@ def test_no_cpu_fallback(pkg):
     assert e.value.code == pkg.ERR_NO_DEVICE
 
 
+def test_library_and_torch_share_one_hip_runtime(pkg):
+    # two HIP runtimes in one process (the library's from its RUNPATH, torch's own) cannot both open the device: the
+    # one initialised second reports "no HIP device".  The pkg fixture imports torch first, so the library binds to it.
+    import torch  # noqa: F401
+    pkg.lib()
+    with open("/proc/self/maps") as f:
+        runtimes = {line.split()[-1] for line in f if "libamdhip64" in line}
+    assert len(runtimes) == 1, runtimes
+
+
 def test_product_never_touches_oracle():
     # the product path must not import, link or call anything under oracle/
     pkg_dir = os.path.join(ROOT, "csv-simd_amd")

@@ -106,6 +106,35 @@ def test_closed_form_check_can_fail(bench):
     assert bench.closed_form_compare(_StubShard(torch, data, lo, tape2, width), tape2.size) is False
 
 
+def test_dump_outputs_are_exact_bounded_and_repeatable(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float64 files that hold the last step's tape exactly (head, tail, a seeded stratified sample, block
+    sums over every entry) and its record, under 64 MB, the same positions on every run; with N > 1 one set per rank."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ENTRIES", 1000)
+    count = 123_457
+    tape = np.sort(np.random.default_rng(5).choice(8 << 30, size=count, replace=False)).astype(np.int64)
+    sb = _StubShard(torch, np.zeros(16, dtype=np.uint8), 0, tape)
+    state = {"count": count, "inq": 0, "base": 1, "total": count + 1, "final": 1}
+    bench.dump_outputs(str(tmp_path / "a"), sb, state, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), sb, state, 0, 1)
+    names = ("record", "tape_head", "tape_tail", "tape_sample_index", "tape_sample", "tape_block_sums")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(f"{n}.npy" for n in names)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) < 64 << 20
+    assert got["record"].tolist() == [count, 0, 1, count + 1, 1]
+    assert np.array_equal(got["tape_head"], tape[:1000]) and np.array_equal(got["tape_tail"], tape[-1000:])
+    idx = got["tape_sample_index"].astype(np.int64)
+    assert idx.size == 1000 and np.all(np.diff(idx) > 0) and idx[-1] < count
+    assert np.array_equal(got["tape_sample"], tape[idx])
+    assert got["tape_block_sums"].sum() == tape.sum() and got["tape_block_sums"].size <= 1000
+    for n in names:                                  # the same arguments: the same files
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+    bench.dump_outputs(str(tmp_path / "c"), sb, state, 1, 2)
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == sorted(f"rank1_{n}.npy" for n in names)
+    assert np.load(tmp_path / "c" / "rank1_tape_head.npy").size == 500
+
+
 def test_cpu_baseline_variants_time_the_same_bytes(bench, pkg, oracle):
     """The CPU legs of the bench line (rank 0 at every N): every variant of BASELINE.md §2 runs on the same host
     sample and finds the same entries; the multi-threaded one states the cores it used."""
